@@ -6,21 +6,29 @@ step = the whole upload-path signature work for the batch
 (fdfs_gpu_sig_batch, FDFS_SIG_HASH: CRC32 + INIT/CALC/FINISH_HASH_CODES4 +
 STORAGE_GEN_FILE_SIGNATURE for every file) followed by the bulk dedup of the
 step's signatures across all ranks (bucket -> RCCL all-to-all -> group ->
-all-to-all back).  Weak scaling: every rank owns its own batch.  The same
-line carries "dedup_100m": config 5's 100M-signature dedup split over the
-run's ranks (strong scaling), so the 1/2/4/8-GPU runs of the default bench
-give the dedup scaling curve too, and "large_file": config 4 (8 x 1 GiB per
-GPU, CRC32 only, the segmented crc_seg_kernel) -- the north star's
-large-file corpus -- with its own roofline and CPU baseline.
+all-to-all back).  Weak scaling: every rank owns its own batch.
 
 Other workloads: --config c3 (MD5 method, 1-4 MiB files), c4 (1 GiB files,
 CRC-only segmented path), c5 (dedup only, 100M signatures, strong scaling).
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with a
-"roofline" object for the dominant kernel (its duration measured by HIP
-events recorded inside libfdfs_gpu on the launch stream) and a
-"cpu_baseline" object (the C oracle of the reference loops on host cores,
-over a bounded sample: at most 4 GiB copied to the host, repeated to ~10 s).
+A plain run sets up the batch, warms up, times --steps steps and prints ONE
+JSON line on rank 0: "value", "ms_per_step" and a "roofline" object for the
+dominant kernel (its duration measured by HIP events recorded inside
+libfdfs_gpu on the launch stream during the timed steps themselves).
+--dump-outputs DIR then writes what the last timed step returned to its
+caller as DIR/<name>.npy (dump_outputs below).
+
+--full adds everything that takes runs of its own: the "cpu_baseline" object
+(the C oracle of the reference loops on host cores, over a bounded sample: at
+most 4 GiB copied to the host, repeated to ~10 s), the chain-floor timings
+and the dedup-only rate of the roofline, and on the default (config 2) line
+the sub-records "photos" (config 3), "upload_mix" (config 1), "dedup_100m"
+(config 5's 100M-signature dedup split over the run's ranks, strong scaling,
+so the 1/2/4/8-GPU runs give the dedup scaling curve too) and "large_file"
+(config 4: 8 x 1 GiB per GPU, CRC32 only, the segmented crc_seg_kernel --
+the north star's large-file corpus -- with its own roofline and CPU
+baseline); at N > 1 also the RCCL-against-torch.distributed check of the
+exchange and the xGMI byte counts.
 """
 from __future__ import annotations
 
@@ -69,6 +77,12 @@ def parse():
     p.add_argument("--exchange", default="rccl", choices=["rccl", "torch"],
                    help="N>1 dedup exchange: libfdfs_gpu's fdfs_gpu_dedup_global over its own RCCL "
                         "communicator, or the same steps over torch.distributed")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what takes runs of its own: CPU baselines, chain floors, the "
+                        "dedup-only rate, the other configs as sub-records of the default line, and "
+                        "at N > 1 the exchange check and xGMI bytes")
+    p.add_argument("--dump-outputs", default="", metavar="DIR",
+                   help="after the timed steps, write the last step's outputs as DIR/<name>.npy")
     return p.parse_args()
 
 
@@ -120,6 +134,32 @@ def timed(fn, steps, warmup, world):
     return max_over_ranks(time.perf_counter() - t0, world)
 
 
+DUMP_BYTES = 60_000_000  # --dump-outputs: array bytes in all (under 64 MB with the .npy headers)
+
+
+def dump_outputs(outdir, outputs):
+    """Write {name: device tensor} (what the last timed step returned) as
+    outdir/<name>.npy.  Every value is an integer: 1- and 2-byte types go out
+    as float32, wider ones as float64 (the int64 outputs are record indices,
+    far below 2^53), both exact; "crc" holds the uint32 bit pattern.  Each
+    array gets an equal share of DUMP_BYTES; a larger one is cut to a fixed
+    seeded sample of its rows (sorted row indices, default_rng(0)), the same
+    rows in every run."""
+    os.makedirs(outdir, exist_ok=True)
+    cap = DUMP_BYTES // max(len(outputs), 1)
+    for name, t in outputs.items():
+        wide = t.element_size() > 2
+        row = max(t[0].numel(), 1) * (8 if wide else 4) if t.shape[0] else 1
+        keep = cap // row
+        if t.shape[0] > keep:
+            rows = np.sort(np.random.default_rng(0).choice(t.shape[0], size=keep, replace=False))
+            t = t[torch.from_numpy(rows).to(t.device)]
+        a = t.cpu().numpy()
+        if name == "crc":
+            a = a.view(np.uint32)
+        np.save(os.path.join(outdir, f"{name}.npy"), a.astype(np.float64 if wide else np.float32))
+
+
 COMM = None  # fastdfs_amd.api.Comm of the run (N > 1, --exchange rccl)
 PACKED = False  # --answers packed
 
@@ -130,6 +170,20 @@ def dedup_step(ctx, sig, gidx, world, stats=None):
     # one GPU holds the whole ingest in order: the ingest index is the
     # position (gidx NULL in fdfs_gpu_dedup, the same answers as arange)
     return ctx.dedup_packed(sig) if PACKED else ctx.dedup(sig)
+
+
+def named_outputs(crc, sig, answers):
+    """The arrays a step hands its caller, by name (dump_outputs)."""
+    out = {}
+    if crc is not None:
+        out["crc"] = crc
+    if sig is not None:
+        out["sig"] = sig
+    if isinstance(answers, tuple):
+        out["dedup_rep"], out["dedup_ref"] = answers
+    elif answers is not None:
+        out["dedup_packed"] = answers
+    return out
 
 
 def cgroup_cpus() -> float | None:
@@ -331,17 +385,24 @@ def peer_bytes(ctx, sig, gidx, world):
     return float(stats.get("row_bytes", 0)), float(stats.get("answer_bytes", 0))
 
 
-def dedup_strong(ctx, sig, gidx, world, steps, warmup):
+def dedup_strong(ctx, sig, gidx, world, steps, warmup, last=None, full=True):
     """Timed dedup steps over one signature set (all ranks): (seconds for
     `steps`, mean ms of the rank's dedup_group kernels, bytes all ranks sent
-    to peers per step over xGMI)."""
+    to peers per step over xGMI: counted by one more call, --full only).
+    `last`, a dict, receives each step's answers by name."""
     ctx.reserve(0, 2 * sig.shape[0])
     ctx.set_timing(True)
     ctx.read_timing(_lib.KERNEL_DEDUP)
-    dt = timed(lambda: dedup_step(ctx, sig, gidx, world), steps, warmup, world)
+
+    def step():
+        answers = dedup_step(ctx, sig, gidx, world)
+        if last is not None:
+            last["out"] = named_outputs(None, None, answers)
+
+    dt = timed(step, steps, warmup, world)
     kms, launches = ctx.read_timing(_lib.KERNEL_DEDUP)
     ctx.set_timing(False)
-    rows, answers = peer_bytes(ctx, sig, gidx, world)
+    rows, answers = peer_bytes(ctx, sig, gidx, world) if full else (0.0, 0.0)
     peer = {"rows": sum_over_ranks(rows, world), "answers": sum_over_ranks(answers, world)}
     return dt, kms / max(launches, 1), peer
 
@@ -470,12 +531,14 @@ def c4_workload(n):
 
 
 def batch_line(args, ctx, world, rank, dev, config, sizes, method, workload, steps, warmup, threads,
-               variant, traffic_ok):
+               variant, traffic_ok, last=None):
     """One signature workload (configs 1-4): a batch per rank resident in
     HBM, `steps` timed steps of fdfs_gpu_sig_batch (+ the global dedup of the
     step's signatures when the method makes them); the dominant kernel's
-    mean duration from the library's HIP events on its launch stream; the
-    CPU baseline on rank 0 at N = 1.  The batch is freed on return."""
+    mean duration from the library's HIP events on its launch stream.  With
+    --full also the chain floors, the dedup-only rate and, on rank 0 at
+    N = 1, the CPU baseline.  `last`, a dict, receives each step's outputs
+    by name.  The batch is freed on return."""
     n = len(sizes)
     kernel, kname = KERNEL_OF[method]
     if method == F.SIG_CRC_ONLY and n > ctx.crc_lane_min_files():
@@ -493,8 +556,9 @@ def batch_line(args, ctx, world, rank, dev, config, sizes, method, workload, ste
 
     def step():
         crc, sig, _ = ctx.sig_batch(data, offs_t, sizes_t, method=method, check_bounds=False)
-        if sig is not None:
-            dedup_step(ctx, sig, gidx, world)
+        answers = dedup_step(ctx, sig, gidx, world) if sig is not None else None
+        if last is not None:
+            last["out"] = named_outputs(crc, sig, answers)
 
     for _ in range(warmup):
         step()
@@ -527,21 +591,23 @@ def batch_line(args, ctx, world, rank, dev, config, sizes, method, workload, ste
         # lane-per-file batches whose dependent chains (MD5 / ELFHash)
         # outlast the HBM stream: the roof is the chain's hardware cost
         # (chain_roof); the largest file timed alone on
-        # the batch's own path stays beside it as a second figure
-        fms, fbytes = chain_floor_ms(ctx, data, offs_t, sizes_t, sizes, method, kernel)
+        # the batch's own path stays beside it as a second figure (--full:
+        # it takes launches of its own)
         hw = chain_roof(method, sizes, torch.cuda.get_device_properties(dev).multi_processor_count, avg_ms)
-        roof.update({"hbm_frac": round(achieved / HBM_PEAK_GBS, 4),
-                     "chain_floor_ms": round(fms, 3), "chain_floor_file_bytes": fbytes,
-                     "chain_floor_frac": round(fms / avg_ms, 4),
-                     "chain_floor_note": "the same kernel over a batch holding the largest file "
-                                         "alone on the path it takes in the batch (one lane's serial "
-                                         "chain; the other files of that timing batch are empty)"})
+        roof["hbm_frac"] = round(achieved / HBM_PEAK_GBS, 4)
+        if args.full:
+            fms, fbytes = chain_floor_ms(ctx, data, offs_t, sizes_t, sizes, method, kernel)
+            roof.update({"chain_floor_ms": round(fms, 3), "chain_floor_file_bytes": fbytes,
+                         "chain_floor_frac": round(fms / avg_ms, 4),
+                         "chain_floor_note": "the same kernel over a batch holding the largest file "
+                                             "alone on the path it takes in the batch (one lane's serial "
+                                             "chain; the other files of that timing batch are empty)"})
         if hw:
             roof.update(hw)
-        else:  # no committed microbenchmark run: the round-5 self-referential roof
+        elif args.full:  # no committed microbenchmark run: the round-5 self-referential roof
             roof.update({"bound": "md5_chain" if method == F.SIG_MD5 else "elf_chain",
                          "peak": round(per_launch / (fms * 1e-3) / 1e9, 1), "frac": round(fms / avg_ms, 4)})
-        if method == F.SIG_MD5 and config != "c4":
+        if args.full and method == F.SIG_MD5 and config != "c4":
             ams, _ = chain_floor_ms(ctx, data, offs_t, sizes_t, sizes, method, kernel, alone=True)
             roof["md5_alone_floor_ms"] = round(ams, 3)
             roof["md5_alone_note"] = ("the largest file as a one-file batch: its CRC moves to the "
@@ -550,7 +616,7 @@ def batch_line(args, ctx, world, rank, dev, config, sizes, method, workload, ste
     valu = load_valu(config, avg_ms) if not args.method else None
     if valu:
         out["valu"] = valu
-    if method != F.SIG_CRC_ONLY:
+    if args.full and method != F.SIG_CRC_ONLY:
         # dedup-only throughput of the same signatures (files/s, all ranks)
         _, sig, _ = ctx.sig_batch(data, offs_t, sizes_t, method=method, check_bounds=False)
         ddt = timed(lambda: dedup_step(ctx, sig, gidx, world), steps, 1, world)
@@ -560,7 +626,7 @@ def batch_line(args, ctx, world, rank, dev, config, sizes, method, workload, ste
                      "method": {0: "crc_only", 1: "hash", 2: "md5"}[method],
                      "crc_variant": "unsigned" if variant else "signed", "align": args.align,
                      "parallelism": f"dp{world} (files sharded, dedup all-to-all)"}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         offs_np = C.layout(sizes, args.align)[0]
         cb = cpu_baseline(data, offs_np, sizes, method, variant, args.cpu_seconds, threads)
         one = cpu_baseline(data, offs_np, sizes, method, variant, args.cpu_seconds / 2, 1)
@@ -635,7 +701,13 @@ def main():
     PACKED = args.answers == "packed"
     rccl_check = None
     if world > 1 and args.exchange == "rccl":
-        COMM, rccl_check = rccl_exchange_check(ctx, world, rank, dev)
+        if args.full:
+            COMM, rccl_check = rccl_exchange_check(ctx, world, rank, dev)
+        else:  # the communicator alone; an error setting it up ends the run
+            from fastdfs_amd.api import Comm
+            COMM = Comm(ctx)
+    # the last timed step's outputs by name (--dump-outputs; rank 0's share)
+    last = {} if args.dump_outputs and rank == 0 else None
     variant = 1 if args.unsigned_hash else 0
     threads = host_threads(args)
     res = {"metric": METRIC, "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -664,8 +736,10 @@ def main():
             method = METHODS[args.method]
         res.update(batch_line(args, ctx, world, rank, dev, args.config, sizes, method, workload,
                               args.steps, args.warmup, threads, variant,
-                              traffic_ok=args.align == 16 and not args.method))
-        if args.config == "c2" and not args.files and not args.method and args.align == 16:
+                              traffic_ok=args.align == 16 and not args.method, last=last))
+        if last is not None:
+            dump_outputs(args.dump_outputs, last.pop("out"))
+        if args.full and args.config == "c2" and not args.files and not args.method and args.align == 16:
             # configs 3 and 1 ride along, each with its
             # own steps, roofline (the chain roof, hbm_frac beside it) and CPU
             # baseline; config 3's 262 GB batch runs first, before the 100M
@@ -709,7 +783,10 @@ def main():
     else:  # c5: dedup only, strong scaling over a fixed 100M-signature set
         total = args.files or 100_000_000
         sig, gidx = C.c5_signatures(total, world, rank, dev)
-        dt, avg_ms, peer = dedup_strong(ctx, sig, gidx, world, args.steps, args.warmup)
+        dt, avg_ms, peer = dedup_strong(ctx, sig, gidx, world, args.steps, args.warmup, last=last,
+                                        full=args.full)
+        if last is not None:
+            dump_outputs(args.dump_outputs, last.pop("out"))
         res.update({"metric": METRIC, "value": round(total * args.steps / dt, 1),
                     "unit": "files/s", "ms_per_step": round(dt / args.steps * 1e3, 3),
                     "scaling": "strong",
@@ -719,7 +796,7 @@ def main():
                                "answers": ("fdfs_gpu_dedup_packed (16-byte {rep, ref} records)" if PACKED
                                            else "fdfs_gpu_dedup (rep u64[n] + ref u32[n])") if world == 1
                                else "fdfs_gpu_dedup_global (rep u64[n] + ref u32[n])"}})
-        if world > 1:  # all ranks' bytes to peers per step, over the step time
+        if args.full and world > 1:  # all ranks' bytes to peers per step, over the step time
             tot = peer["rows"] + peer["answers"]
             res["xgmi"] = {"bytes_per_step": round(tot), "row_bytes_per_step": round(peer["rows"]),
                            "answer_bytes_per_step": round(peer["answers"]),
@@ -743,7 +820,7 @@ def main():
             if traffic:
                 res["roofline"]["traffic"] = traffic
                 res["roofline"]["traffic_source"] = tsrc
-        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_dedup_baseline(sig, args.cpu_seconds, threads)
         else:
             res["cpu_baseline"] = None

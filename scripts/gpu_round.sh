@@ -24,14 +24,14 @@ if part tests; then
   if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
 fi
 if part bench; then
-  step bench_c2 600 python3 bench.py || exit $?
-  step bench_c3 600 python3 bench.py --config c3 --steps 3 --warmup 1 || exit $?
-  step bench_c4 600 python3 bench.py --config c4 || exit $?
-  step bench_c5 600 python3 bench.py --config c5 --steps 5 --warmup 1 || exit $?
-  step bench_c1 900 python3 bench.py --config c1 --steps 3 --warmup 1 || exit $?
-  step bench_c4_hash 600 python3 bench.py --config c4 --method hash --steps 2 --warmup 1 || exit $?
-  step bench_c4_md5 600 python3 bench.py --config c4 --method md5 --steps 2 --warmup 1 || exit $?
-  step bench_c2_crc 600 python3 bench.py --config c2 --method crc || exit $?
+  step bench_c2 600 python3 bench.py --full || exit $?
+  step bench_c3 600 python3 bench.py --full --config c3 --steps 3 --warmup 1 || exit $?
+  step bench_c4 600 python3 bench.py --full --config c4 || exit $?
+  step bench_c5 600 python3 bench.py --full --config c5 --steps 5 --warmup 1 || exit $?
+  step bench_c1 900 python3 bench.py --full --config c1 --steps 3 --warmup 1 || exit $?
+  step bench_c4_hash 600 python3 bench.py --full --config c4 --method hash --steps 2 --warmup 1 || exit $?
+  step bench_c4_md5 600 python3 bench.py --full --config c4 --method md5 --steps 2 --warmup 1 || exit $?
+  step bench_c2_crc 600 python3 bench.py --full --config c2 --method crc || exit $?
   for c in c1 c2 c3 c4 c5 c4_hash c4_md5 c2_crc; do tail -1 $O/bench_$c.log | cut -c1-300; done
 fi
 if part stats; then
