@@ -6,7 +6,7 @@ bench: ctypes binding, torch-resident batches, multi-GPU orchestration.
 """
 from ._lib import (FILE_SIGNATURE_SIZE, FLAG_UNSIGNED_HASH, LIB_PATH, SIG_CRC_ONLY, SIG_HASH,
                    SIG_MD5)
-from .api import Context, FdfsGpuError
+from .api import INDEX_NONE, Context, DedupIndex, FdfsGpuError
 
 __all__ = ["Context", "FdfsGpuError", "SIG_CRC_ONLY", "SIG_HASH", "SIG_MD5",
-           "FLAG_UNSIGNED_HASH", "FILE_SIGNATURE_SIZE", "LIB_PATH"]
+           "FLAG_UNSIGNED_HASH", "FILE_SIGNATURE_SIZE", "LIB_PATH", "DedupIndex", "INDEX_NONE"]

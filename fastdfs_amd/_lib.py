@@ -74,6 +74,9 @@ EXPORTS = (
     "fdfs_gpu_index_ingest",
     "fdfs_gpu_index_stats",
     "fdfs_gpu_index_slots",
+    "fdfs_gpu_index_remove",
+    "fdfs_gpu_index_lookup",
+    "fdfs_gpu_index_tombstones",
 )
 COMM_ID_BYTES = 128
 FILE_STATE_SIZE = 128  # sizeof(fdfs_gpu_file_state)
@@ -221,4 +224,10 @@ def _bind(path: str) -> ctypes.CDLL:
     L.fdfs_gpu_index_stats.argtypes = [vp, ctypes.POINTER(u64), ctypes.POINTER(u64), ctypes.POINTER(u64)]
     L.fdfs_gpu_index_slots.restype = i32
     L.fdfs_gpu_index_slots.argtypes = [vp, ctypes.POINTER(u64)]
+    L.fdfs_gpu_index_remove.restype = i32
+    L.fdfs_gpu_index_remove.argtypes = [vp, vp, vp, u64, vp, vp, vp, vp]
+    L.fdfs_gpu_index_lookup.restype = i32
+    L.fdfs_gpu_index_lookup.argtypes = [vp, vp, vp, u64, vp, vp, vp]
+    L.fdfs_gpu_index_tombstones.restype = i32
+    L.fdfs_gpu_index_tombstones.argtypes = [vp, ctypes.POINTER(u64)]
     return L

@@ -593,6 +593,10 @@ class Comm:
             pass
 
 
+# rep of a signature the index does not hold: FDFS_GPU_INDEX_NONE (UINT64_MAX) read as int64
+INDEX_NONE = -1
+
+
 class DedupIndex:
     """fdfs_gpu_index: the FastDHT "fid" / "ref" state of an ingest stream,
     kept in HBM across batches (include/fdfs_gpu.h)."""
@@ -612,6 +616,32 @@ class DedupIndex:
                                          ref.data_ptr(), _stream_handle(stream)), "fdfs_gpu_index_ingest")
         return rep, ref
 
+    def remove(self, sig: torch.Tensor, stream=None, want_unlink: bool = False):
+        """A batch of deleted files: (rep int64[n], ref int32[n]) after the
+        whole batch, ref 0 = the class is gone (rep is the source to unlink),
+        rep INDEX_NONE = the signature was not in the index.  want_unlink adds
+        unlink uint8[n]: 1 on the batch's first record of each class this
+        call removed."""
+        n = _check_sig(sig, None)
+        rep = torch.empty(n, dtype=torch.int64, device=sig.device)
+        ref = torch.empty(n, dtype=torch.int32, device=sig.device)
+        unlink = torch.empty(n, dtype=torch.uint8, device=sig.device) if want_unlink else None
+        c = self.ctx
+        c._rc(c._L.fdfs_gpu_index_remove(c._h, self._h, sig.data_ptr(), n, rep.data_ptr(), ref.data_ptr(),
+                                         _ptr(unlink), _stream_handle(stream)), "fdfs_gpu_index_remove")
+        return (rep, ref, unlink) if want_unlink else (rep, ref)
+
+    def lookup(self, sig: torch.Tensor, stream=None):
+        """The index's answer for each record without inserting it: (rep
+        int64[n], ref int32[n]), (INDEX_NONE, 0) where it holds no such class."""
+        n = _check_sig(sig, None)
+        rep = torch.empty(n, dtype=torch.int64, device=sig.device)
+        ref = torch.empty(n, dtype=torch.int32, device=sig.device)
+        c = self.ctx
+        c._rc(c._L.fdfs_gpu_index_lookup(c._h, self._h, sig.data_ptr(), n, rep.data_ptr(), ref.data_ptr(),
+                                         _stream_handle(stream)), "fdfs_gpu_index_lookup")
+        return rep, ref
+
     def stats(self) -> dict:
         cl, rec, un = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
         rc = self.ctx._L.fdfs_gpu_index_stats(self._h, ctypes.byref(cl), ctypes.byref(rec), ctypes.byref(un))
@@ -621,7 +651,12 @@ class DedupIndex:
         rc = self.ctx._L.fdfs_gpu_index_slots(self._h, ctypes.byref(sl))
         if rc:
             raise FdfsGpuError(rc, "fdfs_gpu_index_slots")
-        return {"classes": cl.value, "records": rec.value, "unplaced": un.value, "slots": sl.value}
+        dead = ctypes.c_uint64()
+        rc = self.ctx._L.fdfs_gpu_index_tombstones(self._h, ctypes.byref(dead))
+        if rc:
+            raise FdfsGpuError(rc, "fdfs_gpu_index_tombstones")
+        return {"classes": cl.value, "records": rec.value, "unplaced": un.value, "slots": sl.value,
+                "tombstones": dead.value}
 
     def close(self):
         if getattr(self, "_h", None):

@@ -1000,10 +1000,12 @@ struct fdfs_gpu_index {
     fdfs::IndexTable t{};
     void *mem = nullptr;
     uint64_t records = 0;  // records ingested so far (the implicit ingest index base)
-    uint64_t bound = 0;    // upper bound of the classes in the table (exact after a read-back)
+    // upper bound of the occupied slots, live classes plus tombstones (exact
+    // after a read-back); a remove leaves it alone: live turns into dead
+    uint64_t bound = 0;
     hipEvent_t ev = nullptr;
     bool used = false;
-    // ingest, stats and destroy of one index are serialised here (after the
+    // ingest, remove, lookup, stats and destroy of one index are serialised here (after the
     // calling context's mutex, never before it)
     std::mutex mu;
 };
@@ -1082,10 +1084,12 @@ int fdfs_gpu_index_destroy(fdfs_gpu_index *ix)
     return 0;
 }
 
-// Make room for `n` more classes: read back the exact class count (a sync
-// on the index's last ingest) when the running bound says the batch might
-// not fit, and if it still might, grow the table (twice the slots until it
-// fits) and rehash every class into it.  On failure the index is unchanged.
+// Make room for `n` more classes: read back the exact counts of live
+// classes and tombstones (a sync on the index's last call) when the running
+// bound says the batch might not fit, and if it still might, rehash every
+// live class into a fresh table, which drops the tombstones: of the same
+// size when the live classes plus the batch fit it (compaction), else of
+// twice the slots until they do (growth).  On failure the index is unchanged.
 static int index_make_room(fdfs_gpu_ctx *ctx, fdfs_gpu_index *ix, uint64_t n, hipStream_t st)
 {
     if (ix->bound + n <= index_capacity(ix->t.slots))
@@ -1100,11 +1104,12 @@ static int index_make_room(fdfs_gpu_ctx *ctx, fdfs_gpu_index *ix, uint64_t n, hi
         e = hipMemcpy(c, ix->t.counters, sizeof(c), hipMemcpyDeviceToHost);
     if (e != hipSuccess)
         return fail(ctx, e, "index class count");
-    ix->bound = c[0];
+    const uint64_t live = c[0];
+    ix->bound = live + c[1];
     if (ix->bound + n <= index_capacity(ix->t.slots))
         return 0;
-    uint64_t slots = ix->t.slots;
-    while (index_capacity(slots) < ix->bound + n) {
+    uint64_t slots = ix->t.slots;  // stays as it is when dropping the tombstones is enough
+    while (index_capacity(slots) < live + n) {
         if (slots >= (1ull << 41))
             return ENOMEM;
         slots <<= 1;
@@ -1120,6 +1125,7 @@ static int index_make_room(fdfs_gpu_ctx *ctx, fdfs_gpu_index *ix, uint64_t n, hi
     index_carve(t, mem, slots);
     if ((e = fdfs::launch_index_clear(t.state, slots, st)) == hipSuccess &&
         (e = hipMemcpyAsync(t.counters, ix->t.counters, 32, hipMemcpyDeviceToDevice, st)) == hipSuccess &&
+        (e = fdfs::launch_zero_u32(t.counters + 1, 2, st)) == hipSuccess &&  // no tombstone is copied
         (e = fdfs::launch_index_rehash(ix->t, t, st)) == hipSuccess)
         e = hipStreamSynchronize(st);
     if (e != hipSuccess) {
@@ -1130,6 +1136,7 @@ static int index_make_room(fdfs_gpu_ctx *ctx, fdfs_gpu_index *ix, uint64_t n, hi
     (void)hipFree(ix->mem);
     ix->mem = mem;
     ix->t = t;
+    ix->bound = live;
     return 0;
 }
 
@@ -1195,13 +1202,111 @@ int fdfs_gpu_index_stats(fdfs_gpu_index *ix, uint64_t *classes, uint64_t *record
         return EIO;
     if (hipMemcpy(c, ix->t.counters, sizeof(c), hipMemcpyDeviceToHost) != hipSuccess)
         return EIO;
-    ix->bound = c[0];
+    ix->bound = c[0] + c[1];
     if (classes)
         *classes = c[0];
     if (records)
         *records = ix->records;
     if (unplaced)
         *unplaced = c[2];
+    return 0;
+}
+
+int fdfs_gpu_index_tombstones(fdfs_gpu_index *ix, uint64_t *dead)
+{
+    if (!ix || !dead)
+        return EINVAL;
+    std::lock_guard<std::mutex> lk(ix->mu);
+    DeviceGuard g(ix->device);
+    uint64_t c[4] = {0, 0, 0, 0};
+    if (ix->used && hipEventSynchronize(ix->ev) != hipSuccess)
+        return EIO;
+    if (hipMemcpy(c, ix->t.counters, sizeof(c), hipMemcpyDeviceToHost) != hipSuccess)
+        return EIO;
+    ix->bound = c[0] + c[1];
+    *dead = c[1];
+    return 0;
+}
+
+// The delete path for a batch: the batch grouped on its own, as an ingest
+// groups its batch, then one probe per class of the batch.
+int fdfs_gpu_index_remove(fdfs_gpu_ctx *ctx, fdfs_gpu_index *ix, const uint8_t *sig, uint64_t n, uint64_t *rep_out,
+                          uint32_t *ref_out, uint8_t *unlink_out, void *stream)
+{
+    if (!ctx || !ix || ix->device != ctx->device || n >= 0xFFFFFFFFull)
+        return EINVAL;
+    if (n == 0)
+        return 0;
+    if (!sig || !rep_out || !ref_out)
+        return EINVAL;
+    if ((reinterpret_cast<uintptr_t>(sig) | reinterpret_cast<uintptr_t>(rep_out)) & 7)
+        return EINVAL;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    std::lock_guard<std::mutex> lki(ix->mu);
+    DeviceGuard g(ctx->device);
+    if (!g.ok)
+        return ENODEV;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const size_t dws = dedup_ws_bytes(n);
+    int rc = ensure_ws(ctx, dws + 2 * align_up(8 * n) + 2 * align_up(4 * n), st);
+    if (rc)
+        return rc;
+    WsScope wsc(ctx, st);
+    // calls into one index are ordered whatever their streams
+    if (ix->used && !capturing(st))
+        (void)hipStreamWaitEvent(st, ix->ev, 0);
+    Carve cv{static_cast<char *>(ctx->ws) + dws};
+    uint64_t *rep_pos = cv.take<uint64_t>(n);
+    uint32_t *ref_b = cv.take<uint32_t>(n);
+    uint64_t *res_rep = cv.take<uint64_t>(n);
+    uint32_t *res_ref = cv.take<uint32_t>(n);
+    hipEvent_t a, b;
+    timing_pair(ctx, FDFS_KERNEL_DEDUP, a, b);  // the whole call: grouping, probes, answers
+    hipError_t e = fdfs::launch_dedup_group(sig, 24, nullptr, 0, n, ctx->ws, rep_pos, ref_b, false, st, a, nullptr);
+    if (e == hipSuccess)
+        e = fdfs::launch_index_remove(sig, n, rep_pos, ref_b, ix->t, res_rep, res_ref, rep_out, ref_out, unlink_out,
+                                      st);
+    if (b)
+        (void)hipEventRecord(b, st);
+    if (e != hipSuccess)
+        return fail(ctx, e, "index_remove");
+    if (!capturing(st) && hipEventRecord(ix->ev, st) == hipSuccess)
+        ix->used = true;
+    return 0;
+}
+
+int fdfs_gpu_index_lookup(fdfs_gpu_ctx *ctx, fdfs_gpu_index *ix, const uint8_t *sig, uint64_t n, uint64_t *rep_out,
+                          uint32_t *ref_out, void *stream)
+{
+    if (!ctx || !ix || ix->device != ctx->device || n >= 0xFFFFFFFFull)
+        return EINVAL;
+    if (n == 0)
+        return 0;
+    if (!sig || !rep_out || !ref_out)
+        return EINVAL;
+    if ((reinterpret_cast<uintptr_t>(sig) | reinterpret_cast<uintptr_t>(rep_out)) & 7)
+        return EINVAL;
+    std::lock_guard<std::recursive_mutex> lk(ctx->mu);
+    std::lock_guard<std::mutex> lki(ix->mu);
+    DeviceGuard g(ctx->device);
+    if (!g.ok)
+        return ENODEV;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    // after the index's last ingest or remove, and the next one after this
+    // (no workspace is used)
+    if (ix->used && !capturing(st))
+        (void)hipStreamWaitEvent(st, ix->ev, 0);
+    hipEvent_t a, b;
+    timing_pair(ctx, FDFS_KERNEL_DEDUP, a, b);
+    if (a)
+        (void)hipEventRecord(a, st);
+    hipError_t e = fdfs::launch_index_lookup(sig, n, ix->t, rep_out, ref_out, st);
+    if (b)
+        (void)hipEventRecord(b, st);
+    if (e != hipSuccess)
+        return fail(ctx, e, "index_lookup");
+    if (!capturing(st) && hipEventRecord(ix->ev, st) == hipSuccess)
+        ix->used = true;
     return 0;
 }
 

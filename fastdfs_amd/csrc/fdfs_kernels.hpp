@@ -234,13 +234,18 @@ hipError_t launch_answer_apply(const void *a, const uint32_t *na, uint64_t na_ma
 size_t bucket_ws_elems(uint64_t n);
 
 // incremental dedup index (fdfs_index.hip)
+// A slot is occupied when it is not empty: full (a live class) or dead (the
+// tombstone of a removed class, which keeps its place in the probe chains
+// through it until a rehash drops it).  The host keeps live + dead <= 3/4 of
+// the slots, so every probe ends at an empty slot.
 struct IndexTable {
     uint64_t slots;       // power of two
     uint8_t *keys;        // [slots][24] signatures
     uint64_t *rep;        // [slots] class source (ingest index)
     uint32_t *ref;        // [slots] class size so far
-    uint32_t *state;      // [slots] empty / busy / full
-    uint64_t *counters;   // [4]: classes, -, unplaced classes (table full), -
+    uint32_t *state;      // [slots] empty / busy / full / dead
+    uint64_t *counters;   // [4]: live classes (up on insert, down on remove), dead slots,
+                          //      unplaced classes (table full), -
 };
 hipError_t launch_index_clear(uint32_t *state, uint64_t slots, hipStream_t st);
 hipError_t launch_index_rehash(const IndexTable &from, const IndexTable &to, hipStream_t st);
@@ -248,6 +253,13 @@ hipError_t launch_index_ingest(const uint8_t *sig, const uint64_t *gidx, uint64_
                                const uint64_t *rep_pos, const uint32_t *ref_b, const IndexTable &t,
                                uint64_t *res_rep, uint32_t *res_ref, uint64_t *rep_out, uint32_t *ref_out,
                                hipStream_t st);
+// rep_pos / ref_b: the remove batch grouped on its own (launch_dedup_group);
+// unlink_out may be nullptr
+hipError_t launch_index_remove(const uint8_t *sig, uint64_t n, const uint64_t *rep_pos, const uint32_t *ref_b,
+                               const IndexTable &t, uint64_t *res_rep, uint32_t *res_ref, uint64_t *rep_out,
+                               uint32_t *ref_out, uint8_t *unlink_out, hipStream_t st);
+hipError_t launch_index_lookup(const uint8_t *sig, uint64_t n, const IndexTable &t, uint64_t *rep_out,
+                               uint32_t *ref_out, hipStream_t st);
 
 hipError_t launch_answer_gather(const uint64_t *back, const uint64_t *row_of, uint64_t n, uint64_t *rep_out,
                                 uint32_t *ref_out, hipStream_t st);

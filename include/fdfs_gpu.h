@@ -31,6 +31,9 @@
  *       storage/storage_service.c:2652,2714,2734,2984 -> fdfs_gpu_dedup (1 GPU),
  *       fdfs_gpu_dedup_global (N GPUs over RCCL), or fdfs_gpu_dedup_bucket +
  *       the caller's exchange + fdfs_gpu_dedup_group
+ *   the delete callback's fdht_get_ex1 / fdht_inc_ex -1 / fdht_delete_ex
+ *       storage/storage_service.c:820-990 -> fdfs_gpu_index_remove
+ *       (fdfs_gpu_index_lookup for the get alone)
  *   the per-chunk loop itself (StorageFileContext state across chunks)
  *       storage/storage_service.c:7147-7161, storage/storage_dio.c:465-515,
  *       client/fdfs_crc32.c:67-99 -> fdfs_gpu_state_init / fdfs_gpu_update_batch /
@@ -262,6 +265,55 @@ int fdfs_gpu_index_stats(fdfs_gpu_index *index, uint64_t *classes, uint64_t *rec
                          uint64_t *unplaced);
 /* The table's current slot count (grows as above). */
 int fdfs_gpu_index_slots(fdfs_gpu_index *index, uint64_t *slots);
+
+/* The other half of that protocol: the delete callback
+ * (storage/storage_service.c:820-990) reads the deleted file's signature,
+ * its source id and the source's "ref" (:838, :853, :871), calls
+ * fdht_inc_ex(.., -1, ..) on "ref" (:935) and, when the count reaches 0,
+ * deletes the "fid" and "ref" keys (:953, :962) and unlinks the source file
+ * (:972 onward).  fdfs_gpu_index_remove does this for a batch of n deleted
+ * files (sig: device uint8_t[n*24], 8-byte aligned).  The answers are those
+ * AFTER THE WHOLE BATCH: rep_out[i] (device uint64_t[n]) = the source of
+ * record i's class, ref_out[i] (device uint32_t[n]) = the class size left; 0
+ * means the class is gone from the index and the caller unlinks its source
+ * (:948-989).  Removing more members than a class has clamps at 0, the state
+ * a sequential run ends in (there the surplus deletes find nothing and
+ * return 0, :911-914).  A signature that is not in the index is not an
+ * error: rep_out[i] = FDFS_GPU_INDEX_NONE, ref_out[i] = 0, nothing changes.
+ * unlink_out (device uint8_t[n], or NULL) is 1 on exactly one record, the
+ * batch's first member, of each class this call removed, and 0 everywhere
+ * else, so the caller unlinks each source once.  `records` of
+ * fdfs_gpu_index_stats (the implicit ingest-index base) does not change;
+ * `classes` counts live classes and goes down.  A later ingest of a removed
+ * signature starts a new class: that file is its source, ref counts from 0.
+ *
+ * fdfs_gpu_index_lookup is the plain get (fdht_get_ex1 of :2652 and
+ * :838-871) without inserting: rep_out[i] / ref_out[i] of record i's class
+ * as the index holds it, FDFS_GPU_INDEX_NONE / 0 when it does not.  It
+ * writes nothing into the index.
+ *
+ * A removed class leaves a tombstone in its slot; tombstones count towards
+ * the table's load (<= 3/4 with them) and are dropped when an ingest that
+ * might not fit rehashes the table: into one of the same size when the live
+ * classes plus the batch fit it, else into a larger one, as above.
+ * fdfs_gpu_index_tombstones reads their number (synchronous, like _stats).
+ *
+ * Both calls are asynchronous on `stream`, take the context's lock and then
+ * the index's, and are ordered with the index's ingests and each other
+ * whatever their streams.  Neither allocates or synchronises once the
+ * context's workspace is large enough (remove uses as much as an ingest of n
+ * records, lookup none), so both can be captured in a single-stream hipGraph;
+ * a captured call addresses the table as it was at capture and is void once
+ * an ingest has rehashed it (the slot count changed, or tombstones went back
+ * to 0).  EINVAL: NULL ctx / index / sig / rep_out / ref_out with n > 0, sig
+ * or rep_out not 8-byte aligned, an index of another device, n >=
+ * 0xFFFFFFFF; n == 0 returns 0. */
+#define FDFS_GPU_INDEX_NONE UINT64_MAX
+int fdfs_gpu_index_remove(fdfs_gpu_ctx *ctx, fdfs_gpu_index *index, const uint8_t *sig, uint64_t n,
+                          uint64_t *rep_out, uint32_t *ref_out, uint8_t *unlink_out, void *stream);
+int fdfs_gpu_index_lookup(fdfs_gpu_ctx *ctx, fdfs_gpu_index *index, const uint8_t *sig, uint64_t n,
+                          uint64_t *rep_out, uint32_t *ref_out, void *stream);
+int fdfs_gpu_index_tombstones(fdfs_gpu_index *index, uint64_t *dead);
 
 /* Multi-GPU dedup in one call, over RCCL (xGMI between the GPUs of a node):
  * one process per GPU, each holding its share of the ingest (sig, gidx: the
