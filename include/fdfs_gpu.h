@@ -189,7 +189,10 @@ int fdfs_gpu_final_batch(fdfs_gpu_ctx *ctx, const fdfs_gpu_file_state *states,
 /* crc32_combine: out[i] = the CRC32_ex running value of A || B given
  * crc_a[i] = CRC32_ex(A, init) and crc_b[i] = CRC32_ex(B, 0), with len_b[i] =
  * |B| (device arrays): M^(8 |B|) crc_a XOR crc_b over GF(2).  Joins the
- * partial states of one file hashed in pieces on several GPUs. */
+ * partial states of one file hashed in pieces on several GPUs.
+ * Every len_b[i] must be below 2^48 bytes (256 TiB): the advance uses the 48
+ * stored powers M^(8 * 2^k), k < 48, and ignores higher bits of the length.
+ * The call does not check this (it reads nothing back from the device). */
 int fdfs_gpu_crc_combine(fdfs_gpu_ctx *ctx, const uint32_t *crc_a, const uint32_t *crc_b,
                          const uint64_t *len_b, uint32_t n, uint32_t *out, void *stream);
 
@@ -395,7 +398,11 @@ int fdfs_gpu_dedup_global_stats(fdfs_gpu_ctx *ctx, uint64_t *row_bytes, uint64_t
  * called inside a stream capture it returns EINVAL before any collective is
  * enqueued (a captured collective would not run, so no rank could be told);
  * every rank must call it outside a capture.  EIO (a failed launch or RCCL
- * call) leaves the communicator unusable. */
+ * call) leaves the communicator unusable.
+ * File sizes and piece sizes (here and in fdfs_gpu_crc_batch_global_local
+ * below) must be below 2^48 bytes, the bound of fdfs_gpu_crc_combine's len_b
+ * (the same GF(2) advance carries each piece to the end of its file); larger
+ * ones are not detected. */
 int fdfs_gpu_crc_batch_global(fdfs_gpu_ctx *ctx, void *comm, const fdfs_gpu_batch *pieces,
                               const uint64_t *piece_file, const uint64_t *piece_start,
                               const uint64_t *file_size, uint64_t nfiles, uint32_t *crc_out, void *stream);

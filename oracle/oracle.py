@@ -70,6 +70,8 @@ def lib():
         L.orc_md5_init.argtypes = [u8p]
         L.orc_md5_update.argtypes = [u8p, u8p, ctypes.c_size_t]
         L.orc_md5_final.argtypes = [u8p, u8p]
+        L.orc_sig_pack.restype = None
+        L.orc_sig_pack.argtypes = [ctypes.c_int64, ctypes.c_int, u8p, u8p]
         _lib = L
     return _lib
 
@@ -147,6 +149,165 @@ def dio_batch(base: np.ndarray, offset: np.ndarray, size: np.ndarray, method: in
                              _ptr(crc), _ptr(sig), nthreads)
     assert rc == 0
     return crc, sig
+
+
+# ---- host model of fdfs_gpu_file_state (include/fdfs_gpu.h) ----------------
+# The per-upload state StorageFileContext carries between chunks
+# (storage/storage_nio.h:94-96), advanced with the oracle's own primitives, and
+# its 128-byte image as the GPU library lays it out.  Tests write states with
+# it, upload them, and compare what the kernels leave with what it holds.
+
+FILE_STATE_SIZE = 128
+_ST_CRC, _ST_CODES, _ST_MD5, _ST_COUNT, _ST_BUF, _ST_RESERVED = 0, 4, 20, 36, 44, 108
+
+
+class _Md5Ctx(ctypes.Structure):  # orc_md5_ctx
+    _fields_ = [("state", ctypes.c_uint32 * 4), ("count", ctypes.c_uint64),
+                ("buffer", ctypes.c_uint8 * 64)]
+
+
+class FileState:
+    """crc: CRC32_ex running value (int32); h: file_hash_codes (4 int32);
+    md5: orc_md5_ctx, whose count (bytes) is kept for every method."""
+    __slots__ = ("crc", "h", "md5")
+
+    @property
+    def count(self) -> int:
+        return int(self.md5.count)
+
+    @property
+    def pending(self) -> bytes:
+        """The (count % 64) bytes my_md5_update holds back."""
+        return bytes(self.md5.buffer[: self.count & 63])
+
+    def copy(self) -> "FileState":
+        st = FileState()
+        st.crc, st.h = self.crc, list(self.h)
+        st.md5 = _Md5Ctx.from_buffer_copy(self.md5)
+        return st
+
+    def fields(self, method: int) -> tuple:
+        """The fields include/fdfs_gpu.h defines for `method`, comparable."""
+        out = (self.crc, self.count)
+        if method == METHOD_HASH:
+            out += (tuple(self.h),)
+        elif method == METHOD_MD5:
+            out += (tuple(self.md5.state), self.pending)
+        return out
+
+
+def state_init() -> FileState:
+    """storage_write_to_file: CRC32_XINIT, INIT_HASH_CODES4, my_md5_init."""
+    st = FileState()
+    st.crc = -1
+    st.h = [-1, 0, 0, 0]
+    st.md5 = _Md5Ctx()
+    lib().orc_md5_init(ctypes.addressof(st.md5))
+    return st
+
+
+def state_update(st: FileState, data, method: int, variant: int = VARIANT_SIGNED) -> FileState:
+    """dio_write_file's update for one chunk, in place: CRC32_ex always,
+    CALC_HASH_CODES4 for HASH, my_md5_update for MD5, the byte count always."""
+    a = _u8(data)
+    st.crc = crc32_ex(a, st.crc, variant)
+    if method == METHOD_HASH:
+        st.h = [crc32_ex(a, st.h[0], variant), elf_ex(a, st.h[1], variant),
+                simple_ex(a, st.h[2]), time33_ex(a, st.h[3])]
+    if method == METHOD_MD5:
+        lib().orc_md5_update(ctypes.addressof(st.md5), _ptr(a), a.size)
+    else:
+        st.md5.count += a.size
+    return st
+
+
+def state_final(st: FileState, method: int):
+    """dio_write_file's finalisation, as dio_file returns it: (crc32 unsigned,
+    sig24 or None, codes or None).  st is left as it is."""
+    L = lib()
+    crc = L.orc_crc32_final(st.crc) & 0xFFFFFFFF
+    if method == METHOD_CRC_ONLY:
+        return crc, None, None
+    codes = np.zeros(4, np.int32)
+    if method == METHOD_HASH:
+        codes[:] = [L.orc_crc32_final(st.h[0])] + st.h[1:]  # FINISH_HASH_CODES4
+    else:
+        ctx = _Md5Ctx.from_buffer_copy(st.md5)
+        L.orc_md5_final(_ptr(codes), ctypes.addressof(ctx))
+    sig = np.zeros(24, np.uint8)
+    L.orc_sig_pack(st.count, method, _ptr(codes), _ptr(sig))
+    return crc, sig.tobytes(), [int(x) for x in codes]
+
+
+def virtual_prefix(st: FileState, k: int) -> FileState:
+    """As if 64 k more bytes had gone before: the byte count alone rises, in
+    place.  None of the recurrences reads the count (only MD5's final padding
+    and the signature's size field do), and a multiple of 64 leaves the
+    pending bytes where they are."""
+    st.md5.count += 64 * k
+    return st
+
+
+def pack(st: FileState) -> bytes:
+    """The state as fdfs_gpu_file_state (128 bytes): count in bits, low word
+    first; buffer bytes past the pending ones and `reserved` are zero."""
+    out = np.zeros(FILE_STATE_SIZE, np.uint8)
+    out[_ST_CRC:_ST_CODES].view(np.int32)[0] = st.crc
+    out[_ST_CODES:_ST_MD5].view(np.int32)[:] = st.h
+    out[_ST_MD5:_ST_COUNT].view(np.uint32)[:] = list(st.md5.state)
+    out[_ST_COUNT:_ST_BUF].view(np.uint32)[:] = [(8 * st.count) & 0xFFFFFFFF, (8 * st.count) >> 32 & 0xFFFFFFFF]
+    pend = st.pending
+    out[_ST_BUF:_ST_BUF + len(pend)] = np.frombuffer(pend, np.uint8)
+    return out.tobytes()
+
+
+def unpack(raw) -> FileState:
+    """The model of a 128-byte fdfs_gpu_file_state.  Buffer bytes past the
+    pending count and `reserved` are unspecified there and are dropped."""
+    a = _u8(raw)
+    assert a.size == FILE_STATE_SIZE
+    st = FileState()
+    st.crc = int(a[_ST_CRC:_ST_CODES].view(np.int32)[0])
+    st.h = [int(x) for x in a[_ST_CODES:_ST_MD5].view(np.int32)]
+    st.md5 = _Md5Ctx()
+    for i, x in enumerate(a[_ST_MD5:_ST_COUNT].view(np.uint32)):
+        st.md5.state[i] = int(x)
+    lo, hi = (int(x) for x in a[_ST_COUNT:_ST_BUF].view(np.uint32))
+    st.md5.count = (hi << 32 | lo) >> 3
+    for i in range(st.count & 63):
+        st.md5.buffer[i] = int(a[_ST_BUF + i])
+    return st
+
+
+# ---- crc32_combine over GF(2), in plain Python ------------------------------
+
+def crc_zero_advance(v: int, nbytes: int, variant: int = VARIANT_SIGNED) -> int:
+    """M^nbytes v, M the CRC32_ex step over one zero byte (a linear map of the
+    32-bit state for both shift variants): square-and-multiply on M's columns,
+    which are CRC32_ex(b"\\0", 1 << i).  Unsigned 32-bit in and out."""
+    zero = np.zeros(1, np.uint8)
+    m = [crc32_ex(zero, 1 << i, variant) & 0xFFFFFFFF for i in range(32)]
+
+    def apply(cols, x):
+        r = 0
+        for i in range(32):
+            if x >> i & 1:
+                r ^= cols[i]
+        return r
+
+    v &= 0xFFFFFFFF
+    while nbytes:
+        if nbytes & 1:
+            v = apply(m, v)
+        m = [apply(m, c) for c in m]
+        nbytes >>= 1
+    return v
+
+
+def crc32_combine(crc_a: int, crc_b: int, len_b: int, variant: int = VARIANT_SIGNED) -> int:
+    """CRC32_ex(A || B, init) from crc_a = CRC32_ex(A, init), crc_b =
+    CRC32_ex(B, 0) and len_b = |B| (include/fdfs_gpu.h, fdfs_gpu_crc_combine)."""
+    return crc_zero_advance(crc_a, len_b, variant) ^ (crc_b & 0xFFFFFFFF)
 
 
 def gen_files() -> tuple[np.ndarray, np.ndarray, np.ndarray]:

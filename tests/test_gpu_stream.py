@@ -119,11 +119,13 @@ def test_random_chunking_vs_oracle(oracle, ctxs, variant, method):
 def test_state_matches_oracle_mid_stream(oracle, ctxs, method):
     """The state after each chunk is the reference's running state: crc32 =
     CRC32_ex(prefix, XINIT), hash codes = CALC_HASH_CODES4 over the prefix,
-    MD5 count and pending-buffer bytes as my_md5_update leaves them."""
+    MD5 count and pending-buffer bytes as my_md5_update leaves them, and
+    md5_state the words of the oracle's host model (oracle.FileState)."""
     rng = np.random.default_rng(77 + method)
     f = rng.integers(0, 256, size=200_003, dtype=np.uint8)
     ctx = ctxs[0]
     states = ctx.new_states(1)
+    model = oracle.state_init()
     pos = 0
     for c in [5, 59, 0, 64, 1000, 63, 70_000, 1, 128_811]:
         d = torch.from_numpy(f[pos: pos + c].copy() if c else np.zeros(1, np.uint8)).cuda()
@@ -144,6 +146,8 @@ def test_state_matches_oracle_mid_stream(oracle, ctxs, method):
         else:
             r = pos % 64
             assert st[44: 44 + r].tobytes() == f[pos - r: pos].tobytes()
+            oracle.state_update(model, f[pos - c: pos], method, 0)
+            assert [int(x) for x in st[20:36].view(np.uint32)] == list(model.md5.state), pos
     assert pos == f.size
 
 
@@ -206,6 +210,9 @@ def test_crc_combine(oracle, ctxs, variant):
                                     torch.tensor([w[1] for w in want], dtype=torch.int64).cuda())
     got = out.cpu().numpy().view(np.uint32)
     assert [int(x) for x in got] == [w[0] for w in want]
+    # the plain-Python reference of tests/test_gpu_state_resume.py agrees
+    assert [oracle.crc32_combine(a, b, w[1], variant) for a, b, w in zip(a_list, b_list, want)] == \
+        [w[0] for w in want]
 
 
 @pytest.mark.parametrize("method", [1, 2])
