@@ -221,21 +221,27 @@ class Context:
 
     def final_batch(self, states: torch.Tensor, method: int = SIG_HASH,
                     state_idx: torch.Tensor | None = None, want_sig: bool = True,
-                    want_codes: bool = False, stream=None):
+                    want_codes: bool = False, stream=None, crc_out: torch.Tensor | None = None,
+                    sig_out: torch.Tensor | None = None, codes_out: torch.Tensor | None = None):
         """CRC32_FINAL + FINISH_HASH_CODES4 / my_md5_final + the 24-byte
         signature of each state (or of states[state_idx]): (crc int32[n],
-        sig uint8[n,24] | None, codes int32[n,4] | None), as sig_batch."""
+        sig uint8[n,24] | None, codes int32[n,4] | None), as sig_batch
+        (crc_out / sig_out / codes_out: the caller's own outputs, as there)."""
         ns = self._check_states(states)
         n = ns
         if state_idx is not None:
             _check_dev(state_idx, "state_idx", torch.int32)
             n = state_idx.numel()
         dev = states.device
-        crc = torch.empty(n, dtype=torch.int32, device=dev)
-        sig = torch.empty((n, 24), dtype=torch.uint8, device=dev) \
-            if (want_sig and method != SIG_CRC_ONLY) else None
-        codes = torch.empty((n, 4), dtype=torch.int32, device=dev) \
-            if (want_codes and method != SIG_CRC_ONLY) else None
+        crc = torch.empty(n, dtype=torch.int32, device=dev) if crc_out is None else crc_out
+        sig, codes = sig_out, codes_out
+        if method != SIG_CRC_ONLY:
+            if sig is None and want_sig:
+                sig = torch.empty((n, 24), dtype=torch.uint8, device=dev)
+            if codes is None and want_codes:
+                codes = torch.empty((n, 4), dtype=torch.int32, device=dev)
+        else:
+            sig = codes = None
         self._rc(self._L.fdfs_gpu_final_batch(self._h, states.data_ptr(), _ptr(state_idx), n, method,
                                               crc.data_ptr(), _ptr(sig), _ptr(codes),
                                               _stream_handle(stream)), "fdfs_gpu_final_batch")

@@ -532,6 +532,12 @@ int fdfs_gpu_sig_batch(fdfs_gpu_ctx *ctx, const fdfs_gpu_batch *batch, int metho
         return 0;
     if (!batch->base || !batch->offset || !batch->size || !crc_out)
         return EINVAL;
+    // the lanes store a signature as three uint2 and the codes as one int4
+    if (reinterpret_cast<uintptr_t>(crc_out) & 3)
+        return EINVAL;
+    if (method != FDFS_SIG_CRC_ONLY &&
+        (reinterpret_cast<uintptr_t>(sig_out) & 7 || reinterpret_cast<uintptr_t>(codes_out) & 15))
+        return EINVAL;
     std::lock_guard<std::recursive_mutex> lk(ctx->mu);
     if (int rc0 = lane_err_check(ctx))
         return rc0;

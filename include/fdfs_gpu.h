@@ -114,6 +114,9 @@ int fdfs_gpu_reserve(fdfs_gpu_ctx *ctx, uint64_t max_files, uint64_t max_records
  *   codes_out: device int32_t[n*4] or NULL: file_hash_codes after FINISH
  *              (HASH) or the raw MD5 digest (MD5), as StorageFileContext holds
  *              them (storage/storage_nio.h:94).
+ * Alignment: crc_out 4 bytes; sig_out 8 bytes (a record is stored as three
+ * 8-byte words) and codes_out 16 bytes (one 16-byte store per file) when the
+ * method has them.  EINVAL otherwise, before anything is launched or written.
  * Asynchronous on `stream`. */
 int fdfs_gpu_sig_batch(fdfs_gpu_ctx *ctx, const fdfs_gpu_batch *batch, int method,
                        uint32_t *crc_out, uint8_t *sig_out, int32_t *codes_out,

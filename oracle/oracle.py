@@ -26,6 +26,7 @@ VARIANT_UNSIGNED = 1
 METHOD_CRC_ONLY = 0
 METHOD_HASH = 1
 METHOD_MD5 = 2
+FILE_SIG_SIZE = 24
 
 _lib = None
 
@@ -149,6 +150,19 @@ def dio_batch(base: np.ndarray, offset: np.ndarray, size: np.ndarray, method: in
                              _ptr(crc), _ptr(sig), nthreads)
     assert rc == 0
     return crc, sig
+
+
+def codes_from_sig(sig: np.ndarray, method: int) -> np.ndarray:
+    """int32[n,4]: the codes StorageFileContext holds for signatures
+    uint8[n,24] (dio_batch's): HASH, the four big-endian fields at bytes
+    8..24 (int2buff of file_hash_codes after FINISH); MD5, bytes 8..24 as
+    little-endian words (the digest is the state words stored little-endian,
+    which orc_dio_file copies into codes).  tests/test_oracle.py ties it to
+    dio_file's codes."""
+    assert method in (METHOD_HASH, METHOD_MD5)
+    sig = np.ascontiguousarray(sig, dtype=np.uint8).reshape(-1, FILE_SIG_SIZE)
+    words = np.ascontiguousarray(sig[:, 8:]).view(">u4" if method == METHOD_HASH else "<u4")
+    return words.astype(np.uint32).view(np.int32).reshape(-1, 4)
 
 
 # ---- host model of fdfs_gpu_file_state (include/fdfs_gpu.h) ----------------

@@ -42,7 +42,7 @@ def _gpu(ctx, dev_batch, method):
 def _check(oracle, ctx, variant, buf, offs, sizes, methods=METHODS, dev_batch=None):
     dev_batch = dev_batch or _to_dev(buf, offs, sizes)
     for m in methods:
-        crc, sig, _ = _gpu(ctx, dev_batch, m)
+        crc, sig, codes = _gpu(ctx, dev_batch, m)
         ocrc, osig = oracle.dio_batch(buf, offs, sizes, m, variant, nthreads=8)
         bad = np.nonzero(crc != ocrc)[0]
         assert bad.size == 0, (m, variant, bad[:10], sizes[bad[:10]])
@@ -52,6 +52,12 @@ def _check(oracle, ctx, variant, buf, offs, sizes, methods=METHODS, dev_batch=No
             fields = [int(np.any(sig[:, 4 * k:4 * k + 4] != osig[:, 4 * k:4 * k + 4], axis=1).sum())
                       for k in range(6)]
             assert badsig.size == 0, (m, variant, badsig[:10], sizes[badsig[:10]], fields)
+            # codes_out: file_hash_codes after FINISH (HASH) / the digest's words (MD5)
+            ocodes = oracle.codes_from_sig(osig, m)
+            assert codes.dtype == np.int32 and codes.shape == ocodes.shape
+            badcodes = np.nonzero(np.any(codes != ocodes, axis=1))[0]
+            cols = [int((codes[:, k] != ocodes[:, k]).sum()) for k in range(4)]
+            assert badcodes.size == 0, (m, variant, badcodes[:10], sizes[badcodes[:10]], cols)
 
 
 def _packed(sizes, align, rng, slack=0):
@@ -285,17 +291,19 @@ def test_offload_regime_boundary(oracle, ctxs, extra):
     sizes[big] = rng.integers(4 << 20, 6 << 20, 200)
     data, offs_t, sizes_t = C.device_batch(sizes, seed=9 + extra, device="cuda:0")
     ctx = ctxs[0]
-    out = {m: ctx.sig_batch(data, offs_t, sizes_t, method=m) for m in (0, 1, 2)}
+    out = {m: ctx.sig_batch(data, offs_t, sizes_t, method=m, want_codes=True) for m in (0, 1, 2)}
     torch.cuda.synchronize()
     assert torch.equal(out[0][0], out[1][0]) and torch.equal(out[0][0], out[2][0])
     offs = offs_t.cpu().numpy()
     pick = np.concatenate([big[:12], rng.choice(n, size=400, replace=False)])
     for m in (1, 2):
         crc_np, sig_np = out[m][0].cpu().numpy().view(np.uint32), out[m][1].cpu().numpy()
+        codes_np = out[m][2].cpu().numpy()
         for i in pick:
             d = data[int(offs[i]): int(offs[i] + sizes[i])].cpu().numpy()
-            c, s, _ = oracle.dio_file(d, m, 0)
+            c, s, codes = oracle.dio_file(d, m, 0)
             assert c == crc_np[i] and s == sig_np[i].tobytes(), (m, i, sizes[i])
+            assert [int(x) for x in codes_np[i]] == codes, (m, i, sizes[i])
     del data, out
     torch.cuda.empty_cache()
 
@@ -354,15 +362,17 @@ def test_lane_fold_short_files(oracle, ctxs, variant):
     sizes[:2000] = 128 * rng.integers(0, 6, 2000) + rng.integers(-1, 2, 2000).clip(0)
     data, offs_t, sizes_t = C.device_batch(sizes, seed=21 + variant, device="cuda:0", align=1)
     crc0, _, _ = ctx.sig_batch(data, offs_t, sizes_t, method=0)
-    crc1, sig1, _ = ctx.sig_batch(data, offs_t, sizes_t, method=1)
+    crc1, sig1, codes1 = ctx.sig_batch(data, offs_t, sizes_t, method=1, want_codes=True)
     torch.cuda.synchronize()
     assert torch.equal(crc0, crc1)
     crc_np, sig_np = crc1.cpu().numpy().view(np.uint32), sig1.cpu().numpy()
+    codes_np = codes1.cpu().numpy()
     offs = offs_t.cpu().numpy()
     for i in np.concatenate([np.arange(0, 2000, 7), rng.choice(n, size=600, replace=False)]):
         d = data[int(offs[i]): int(offs[i] + sizes[i])].cpu().numpy()
-        c, sg, _ = oracle.dio_file(d, 1, variant)
+        c, sg, codes = oracle.dio_file(d, 1, variant)
         assert c == crc_np[i] and sg == sig_np[i].tobytes(), (i, sizes[i], offs[i] % 16)
+        assert [int(x) for x in codes_np[i]] == codes, (i, sizes[i], offs[i] % 16)
     del data
     torch.cuda.empty_cache()
 
@@ -462,6 +472,11 @@ def test_host_batch_streamed(oracle, ctxs, method):
     assert np.array_equal(crc, ocrc)
     if method:
         assert np.array_equal(sig, osig)
+        ocodes = oracle.codes_from_sig(osig, method)
+        assert codes.dtype == np.int32 and codes.shape == ocodes.shape
+        assert np.array_equal(codes, ocodes), [int((codes[:, k] != ocodes[:, k]).sum()) for k in range(4)]
+    else:
+        assert sig is None and codes is None
     # pinned host memory: the same, one default-size window
     pinned = torch.from_numpy(buf).pin_memory()
     crc2, sig2, _ = ctxs[0].sig_batch_host(pinned, offs, sizes, method=method)

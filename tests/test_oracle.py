@@ -115,6 +115,27 @@ def test_sig_pack_layout(oracle):
     assert sig2[8:] == hashlib.md5(b"hello fastdfs").digest()
 
 
+@pytest.mark.parametrize("variant", [0, 1])
+@pytest.mark.parametrize("method", [1, 2])
+def test_codes_from_sig(oracle, method, variant):
+    """codes_from_sig (the batch-speed reference the GPU tests compare
+    codes_out with) over dio_batch's signatures equals dio_file's own codes,
+    file by file: sizes on both sides of MD5's padding and block boundaries,
+    every byte >= 0x80 so negative codes occur."""
+    rng = np.random.default_rng(500 + 2 * method + variant)
+    sizes = np.array([0, 1, 55, 56, 63, 64, 65, 4096, 200003], np.int64)
+    offs = np.zeros_like(sizes)
+    offs[1:] = np.cumsum(sizes + 3)[:-1]
+    buf = rng.integers(0, 256, size=int(offs[-1] + sizes[-1]), dtype=np.uint8) | 0x80
+    _, sig = oracle.dio_batch(buf, offs, sizes, method, variant)
+    got = oracle.codes_from_sig(sig, method)
+    assert got.dtype == np.int32 and got.shape == (len(sizes), 4)
+    want = [oracle.dio_file(buf[int(o): int(o + s)], method, variant)[2] for o, s in zip(offs, sizes)]
+    for i, w in enumerate(want):
+        assert [int(x) for x in got[i]] == w, (int(sizes[i]), method, variant)
+    assert min(min(w) for w in want) < 0
+
+
 def test_crc_signed_differs_from_zlib_only_when_sign_set(oracle):
     # a state never reaching bit 31 would make the variants agree; they must
     # differ on ordinary data and agree on the empty input.
